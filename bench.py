@@ -47,6 +47,20 @@ roofline_shade_kernel: algorithmic path-state bytes per vertex x vertices / stag
 cpu_baseline (rank 0, N=1 only): the compiled reference's own render_image_nopreviz() on all host
 cores when oracle/_ref/libptref.so is present (kind "reference"), otherwise the oracle's threaded
 restatement (kind "port"), on a bounded sample of the same workload.
+
+--steps K is the number of timed steps, always.  Step s renders samples [s * S, (s + 1) * S) of every pixel (S = samples per step);
+a pixel has 65536 sample streams, so a run with more steps than fit starts over at sample 0 (the line then says after how many
+steps, "sample_windows"): every step still does a full step's work.
+
+--dump-outputs DIR (rank 0, after the timed region): what the timed path handed its caller after the last timed step, as float32 /
+float64 .npy files in DIR, at most 64 MB in all:
+  framebuffer_rgb.npy, framebuffer_weight.npy   the accumulation buffer mipt_render_device adds into (summed over the ranks): colour sums
+        [H, W, 3] and splat weights [H, W], rows as the library stores them (pixel (i, j) at row H - 1 - i); it holds every step of the
+        run, warm-up included.  A frame larger than the budget (4K) is dumped as a fixed sample of pixels (seed DUMP_SEED):
+        framebuffer_pixel_index.npy holds their flat indices (row * W + column, same row order), the two others [n, 3] and [n].
+  last_step_counters.npy   the last timed step's counters (mipt_get_stats, summed over the ranks), in the order of DUMP_COUNTERS.
+The inputs depend on the arguments alone (seeded scene, fixed sample streams), so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -59,6 +73,9 @@ sys.path.insert(0, ROOT)
 
 SPP_PER_PASS = 256          # a quarter of the step at 1080p (the library itself cuts a step into passes of at most 2^30 paths, ~172 GB of path state); scaled down with the pixel count
 SEED_STRIDE = 65536         # sample k of pixel p draws from pcg32(p * 65536 + k): a run may use at most 65536 samples per pixel
+DUMP_MAX_BYTES = 60_000_000     # --dump-outputs: array bytes written at most (64 MB in all with the .npy headers)
+DUMP_SEED = 0                   # --dump-outputs: the fixed pixel sample of a frame too large to dump whole
+DUMP_COUNTERS = ("paths", "rays_closest", "rays_shadow", "mesh_casts_closest", "mesh_casts_shadow")
 
 
 def parse():
@@ -79,7 +96,29 @@ def parse():
     ap.add_argument("--share-gpu", action="store_true", help="functional test: all ranks use GPU 0 (needs --backend gloo)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pmc", action="store_true", help="profiling run: skip the CPU legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's framebuffer and counters to DIR/<name>.npy")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, fb, counters, W, H):
+    """--dump-outputs (see the module text): fb = the host copy of the [W*H*3 rgb | W*H weights] buffer, counters = DUMP_COUNTERS."""
+    import numpy as np
+    npx = W * H
+    rgb, weight = fb[:3 * npx].reshape(npx, 3), fb[3 * npx:4 * npx]
+    arrays = {"last_step_counters": np.asarray(counters, np.float64)}
+    if npx * 16 <= DUMP_MAX_BYTES:
+        arrays["framebuffer_rgb"] = rgb.reshape(H, W, 3)
+        arrays["framebuffer_weight"] = weight.reshape(H, W)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(npx, DUMP_MAX_BYTES // (16 + 8), replace=False))
+        arrays["framebuffer_pixel_index"] = idx.astype(np.float64)
+        arrays["framebuffer_rgb"] = rgb[idx]
+        arrays["framebuffer_weight"] = weight[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "pixels": int(arrays["framebuffer_weight"].size), "sampled": "framebuffer_pixel_index" in arrays}
 
 
 def oracle_bytes_per_ray(mesh, mat, cfg_full):
@@ -208,6 +247,8 @@ def run(args):
     in_process = [int(x) for x in args.in_process.split(",")] if args.in_process else []
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if in_process and world > 1:
         raise SystemExit("--in-process drives its devices from one process: do not launch it under torch.distributed.run")
     if launched and world != args.gpus:
@@ -267,9 +308,13 @@ def run(args):
     SPS = samples_per_step(args.scaling)
     other = "weak" if args.scaling == "strong" else "strong"
     OTHER_STEPS = 2 if job_gpus > 1 else 0
-    total_spp = SPS * (args.steps + args.warmup) + samples_per_step(other) * (OTHER_STEPS + 1)
-    if total_spp > SEED_STRIDE:
-        raise SystemExit(f"{total_spp} samples per pixel in this run, but the streams of neighbouring pixels are {SEED_STRIDE} apart: use fewer steps")
+    other_spp = samples_per_step(other) * (OTHER_STEPS + 1)
+    windows = args.steps + args.warmup          # step s renders sample window s % windows
+    if SPS * windows + other_spp > SEED_STRIDE:
+        windows = (SEED_STRIDE - other_spp) // SPS
+        if windows < 1:
+            raise SystemExit(f"{SPS + other_spp} samples per pixel for one step, but the streams of neighbouring pixels are {SEED_STRIDE} apart: use fewer samples per step")
+    total_spp = SPS * windows + other_spp
     mesh, cfg, mat, wl_text = scenes.workload(args.workload, args.width, args.height, total_spp, args.grid)
     args.width, args.height = cfg.W, cfg.H
 
@@ -324,7 +369,7 @@ def run(args):
 
     stage("warm-up steps")
     for s in range(args.warmup):
-        step(s)
+        step(s % windows)
     sync()
     if in_process:
         STAGE["reduce"] = rt.group_reduce_kind()
@@ -337,7 +382,7 @@ def run(args):
     pipeline = -1
     merged = 0
     for s in range(args.warmup, args.warmup + args.steps):
-        st = step(s)
+        st = step(s % windows)
         rays_c += st["rays_closest"]; rays_s += st["rays_shadow"]; paths += st["paths"]
         kern_ms += st["traverse_ms"]; launches += st["traverse_launches"]
         sh_ms += st["shadow_ms"]; sh_launches += st["shadow_launches"]; shade_ms += st["shade_ms"]; resolve_ms += st["resolve_ms"]
@@ -353,10 +398,18 @@ def run(args):
     reduce_frame()
     sync()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        stage("dump outputs")
+        counters = torch.tensor([float(st[k]) for k in DUMP_COUNTERS], dtype=torch.float64, device=dev if on_device else "cpu")
+        if world > 1:
+            dist.all_reduce(counters, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, accum.cpu().numpy(), counters.cpu().numpy(), args.width, args.height)
     stage("checks")
     other_line = None
     if OTHER_STEPS:                                      # the other scaling mode, beside the timed region
-        o_sps, base = samples_per_step(other), SPS * (args.steps + args.warmup)
+        o_sps, base = samples_per_step(other), SPS * windows
         accum2 = accum.clone()
         step(0, o_sps, base)
         sync()
@@ -406,6 +459,10 @@ def run(args):
         }
         if other_line:
             out["other_scaling"] = other_line
+        if windows < args.warmup + args.steps:
+            out["sample_windows"] = windows
+        if dumped:
+            out["dumped_outputs"] = dumped
         if world == 1 and args.pmc and pipeline == 1:
             out["stage_ms_per_step"] = {("traverse" if merged else "extend"): kern_ms / args.steps, "shadow": sh_ms / args.steps, "generate+shade": shade_ms / args.steps, "resolve": resolve_ms / args.steps}
         if world == 1 and not in_process and not args.pmc:

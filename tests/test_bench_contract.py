@@ -29,8 +29,13 @@ SMALL = ("--steps", "2", "--warmup", "1", "--grid", "160", "--width", "480", "--
 
 
 @pytest.fixture(scope="module")
-def line():
-    return run_bench(*SMALL)
+def dump_dir(tmp_path_factory):
+    return str(tmp_path_factory.mktemp("bench_outputs"))
+
+
+@pytest.fixture(scope="module")
+def line(dump_dir):
+    return run_bench(*SMALL, "--dump-outputs", dump_dir)
 
 
 @pytest.mark.gpu
@@ -116,6 +121,34 @@ def test_live_cpu_baseline_object(line):
 
 
 @pytest.mark.gpu
+def test_live_dump_outputs_hold_the_last_step(line, dump_dir):
+    """--dump-outputs: the framebuffer the timed steps added into and the last step's counters, float32 / float64, under 64 MB."""
+    import numpy as np
+    d = line["dumped_outputs"]
+    assert d["dir"] == dump_dir and not d["sampled"]
+    assert sorted(os.listdir(dump_dir)) == d["files"] == ["framebuffer_rgb.npy", "framebuffer_weight.npy", "last_step_counters.npy"]
+    assert sum(os.path.getsize(os.path.join(dump_dir, f)) for f in d["files"]) <= 64e6
+    rgb = np.load(os.path.join(dump_dir, "framebuffer_rgb.npy"))
+    w = np.load(os.path.join(dump_dir, "framebuffer_weight.npy"))
+    c = np.load(os.path.join(dump_dir, "last_step_counters.npy"))
+    assert rgb.dtype == np.float32 and rgb.shape == (270, 480, 3) and w.dtype == np.float32 and w.shape == (270, 480)
+    assert np.isfinite(rgb).all() and (rgb >= 0).all() and rgb.max() > 0 and (w > 0).all()
+    assert c.dtype == np.float64 and c[0] == 480 * 270 * 32                     # paths of one step: every pixel, --spp-per-step samples
+    ls = line["launch_stats"]
+    assert c[1] + c[2] == pytest.approx((ls["rays_closest"] + ls["rays_shadow"]) / line["steps"], rel=0.05)
+
+
+@pytest.mark.gpu
+def test_steps_beyond_the_sample_streams_are_all_timed():
+    """More steps than a pixel's 65536 sample streams hold: the run starts over at sample 0 and still times every step asked for."""
+    out = run_bench("--steps", "3", "--warmup", "1", "--grid", "32", "--width", "64", "--height", "36", "--spp-per-step", "32768", "--no-cpu-baseline")
+    assert out["steps"] == 3 and out["sample_windows"] == 1 and out["ms_per_step"] > 0
+    rays = out["launch_stats"]["rays_closest"] + out["launch_stats"]["rays_shadow"]
+    assert out["mpaths_per_s"] * out["ms_per_step"] * 1e-3 * 3 == pytest.approx(64 * 36 * 32768 * 3 / 1e6, rel=1e-6)
+    assert rays / (out["ms_per_step"] * 1e-3 * 3) / 1e6 == pytest.approx(out["value"], rel=1e-6)
+
+
+@pytest.mark.gpu
 def test_two_gpus_in_a_child_process_where_two_exist():
     """bench.py --gpus 2 from the plain command line: ONE process, mipt_create(ids, 2), RCCL ncclReduce or a non-zero exit."""
     import torch
@@ -137,6 +170,25 @@ def test_bench_refuses_to_run_without_a_gpu_or_with_fewer_than_asked():
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["value"] is None and d["stage"] == "devices" and "refusing" in d["error"] and d["n_gpus"] == n + 1 and "stages_in_order" in d
+
+
+def test_dump_outputs_keeps_its_budget_and_its_sample(tmp_path):
+    """The dump of a frame too large for 64 MB (4K) is a fixed pixel sample: the same pixels every run, the values those pixels hold."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    W, H = 3840, 2160
+    fb = np.random.default_rng(1).random(W * H * 4, dtype=np.float32)
+    d = bench.dump_outputs(str(tmp_path / "a"), fb, [1.0, 2.0, 3.0, 4.0, 5.0], W, H)
+    bench.dump_outputs(str(tmp_path / "b"), fb, [1.0, 2.0, 3.0, 4.0, 5.0], W, H)
+    assert d["sampled"] and sum(os.path.getsize(tmp_path / "a" / f) for f in d["files"]) <= 64e6
+    got = {f: np.load(tmp_path / "a" / f) for f in d["files"]}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert all((got[f] == np.load(tmp_path / "b" / f)).all() for f in d["files"])
+    idx = got["framebuffer_pixel_index.npy"].astype(np.int64)
+    assert len(np.unique(idx)) == len(idx) == d["pixels"] and idx.max() < W * H
+    assert (got["framebuffer_rgb.npy"] == fb[:3 * W * H].reshape(-1, 3)[idx]).all()
+    assert (got["framebuffer_weight.npy"] == fb[3 * W * H:][idx]).all()
 
 
 def test_source_hash_is_stable_and_sees_the_flags():
